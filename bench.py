@@ -1,6 +1,7 @@
 """bench.py -- GN iterations / second of the 8-keyframe 640x480 photometric window BA on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--window 1|4] [--dtype f64|f32] [--keyframes B] [--replicas] [--no-cpu]
+                    [--dump-outputs DIR]
     (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`; a plain
      `python bench.py --gpus N` with no WORLD_SIZE in the environment starts its N ranks itself, see self_launch)
 
@@ -27,6 +28,8 @@ top-level `cpu_baseline` (the oracle on the SAME dense workload) all describe th
 odometry loop (tracking + keyframe management + DepthCov network + window BA, como_amd/odom/sequential.py <-> the reference's
 como/odom/sequential/ComoSeq.py:42-127), no collective; K = frames timed per rank after the two-frame initialisation and W
 warm-up frames; value = sum over ranks of frames / s ("scaling": "weak").
+--dump-outputs DIR writes what the headline leg's last timed step computed to DIR/<name>.npy (float64, see dump_outputs): the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -291,6 +294,26 @@ def timed_steps(wb, steps, barrier=None):
     return time.perf_counter() - t0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wb, out_dir):
+    """What the last timed step of `wb` computed, as a caller of the iteration receives it (Mapping.iterate): the state after the
+    update (WindowBA.snapshot_state: frame poses, affine parameters, landmarks, median depths and, on the fused chain, the
+    scaffold's projected landmarks / log-depths) and the step's update `delta` -> out_dir/<name>.npy, float64.  Must run before
+    any further iteration of `wb` (the roofline and the process-group record iterate it again)."""
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().cpu().double().numpy() for k, v in wb.snapshot_state(torch.float64).items()}
+    arrays["delta"] = wb.delta.detach().cpu().double().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} ({total} bytes) to {out_dir}", file=sys.stderr, flush=True)
+
+
 def block_kernel_roofline(wb, dtype_name, reps=5):
     """Dominant kernel (the pair-block kernel): duration from HIP events on the launch stream (events cannot sit inside a
     captured graph, so the same kernel on the same data is timed in eager iterations right after the timed region;
@@ -538,7 +561,13 @@ def main():
     ap.add_argument("--replicas", action="store_true", help="config 5: one SEQUENCE per GPU through the whole odometry loop, no collective (weak scaling)")
     ap.add_argument("--force-shard", action="store_true", help="testing on a one-GPU box: run the multi-GPU code path (RCCL "
                     "collectives, sharded medians, fixed-point exchange) through a single-rank process group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.replicas:
+        ap.error("--dump-outputs covers the window-BA leg, not --replicas")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: nobody started the ranks -- start them here (one process per GPU under
@@ -569,6 +598,8 @@ def main():
         print("hipGraph capture failed:", getattr(wb, "capture_error", "?"), file=sys.stderr)
     elapsed = shard.max_scalar(timed_steps(wb, args.steps, barrier=shard.barrier), device)
     ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and shard.rank == 0:
+        dump_outputs(wb, args.dump_outputs)
     roof = block_kernel_roofline(wb, args.dtype)
     import como_amd.odom.backend.linear_system as lin_sys
     info = int(lin_sys.solve_system.last_info)

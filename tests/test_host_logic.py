@@ -447,6 +447,35 @@ def test_window_state_lives_in_one_buffer_and_snapshot_is_a_copy():
     assert sn["poses"].dtype == torch.float64 and w.snapshot_state(torch.float32)["poses"].dtype == torch.float32
 
 
+def test_bench_dump_outputs_writes_the_snapshot_and_update(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: what a caller of the iteration receives -- `snapshot_state` and the step's `delta` -- lands in
+    DIR/<name>.npy as float64 with the same values (a CPU window stands in for the GPU one)."""
+    import copy
+    import os
+    import numpy as np
+    from como_amd import synth
+    from como_amd.odom.window_ba import WindowBA, DEFAULT_CFG
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    B, m = 3, 16
+    eye = torch.eye(m, dtype=torch.float64)[None].repeat(B, 1, 1)
+    g = torch.Generator().manual_seed(0)
+    st = synth.make_window(B=B, H=48, W=64, m=m, dtype=torch.float64, device="cpu", seed=1,
+                           predictor=lambda cov, cm: (eye, eye, torch.rand((B, 48, 64, m), generator=g, dtype=torch.float64)))
+    cfg = copy.deepcopy(DEFAULT_CFG)
+    cfg["photo_construction"]["nonmax_suppression_window"] = 4
+    w = WindowBA(st, cfg=cfg, pix_dtype=torch.float64, window_full=True, fused=False)
+    w.delta = torch.linspace(-1.0, 1.0, 8 * B + 3 * int(w.P_m.shape[0]), dtype=torch.float64)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    out = tmp_path / "dump"
+    bench.dump_outputs(w, str(out))
+    want = dict(w.snapshot_state(torch.float64), delta=w.delta)
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        a = np.load(out / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, v.numpy())
+
+
 def test_cached_coordinate_helpers_and_pose_composition_equal_the_plain_forms():
     """Host-side helpers of the keyframe path: the cached normalisation constants / pixel grids return what the uncached
     expressions give (reference como/utils/coords.py:12-15, 31-36), and `composeSE3`'s torch form (CPU tensors; the GPU path is
