@@ -357,11 +357,11 @@ int como_frame_stack_f64(const void* rgb, int rgb_is_f32, int H, int W, double* 
 
 
 /* The tracker's three-level image pyramid of one colour frame (3,H,W) in one launch -- gray (H,W), l1 (ceil(H/2),ceil(W/2)), l2 (half of
- * that again): bit-identical to como_rgb_to_gray_f32 + 2 x como_img_blur_down_f32.  zero_ptrs / zero_bytes (n_zero <= 8, 16-byte
+ * that again): bit-identical to como_rgb_to_gray_f32 + 2 x como_img_blur_down_f32.  zero_ptrs_host / zero_bytes_host (n_zero <= 8, 16-byte
  * aligned, multiples of 16 bytes): buffers cleared in the same launch. */
-int como_track_frame_pyramid3_f32(const float* rgb, float* gray, float* l1, float* l2, int H, int W, void* const* zero_ptrs,
-                                  const long* zero_bytes, int n_zero, como_stream_t stream) {
-  if (!rgb || !gray || !l1 || !l2 || H < 4 || W < 4 || n_zero < 0 || n_zero > 8 || (n_zero && (!zero_ptrs || !zero_bytes)))
+int como_track_frame_pyramid3_f32(const float* rgb, float* gray, float* l1, float* l2, int H, int W, void* const* zero_ptrs_host,
+                                  const long* zero_bytes_host, int n_zero, como_stream_t stream) {
+  if (!rgb || !gray || !l1 || !l2 || H < 4 || W < 4 || n_zero < 0 || n_zero > 8 || (n_zero && (!zero_ptrs_host || !zero_bytes_host)))
     return COMO_ERR_ARG;
   como::ZeroList z;
   z.n = n_zero;
@@ -369,9 +369,10 @@ int como_track_frame_pyramid3_f32(const float* rgb, float* gray, float* l1, floa
   for (int k = 0; k < 8; ++k) {
     z.p[k] = nullptr; z.n16[k] = 0;
     if (k < n_zero) {
-      if (!zero_ptrs[k] || ((uintptr_t)zero_ptrs[k] & 15) || zero_bytes[k] < 0 || (zero_bytes[k] & 15)) return COMO_ERR_ARG;
-      z.p[k] = (uint4*)zero_ptrs[k];
-      z.n16[k] = zero_bytes[k] / 16;
+      if (!zero_ptrs_host[k] || ((uintptr_t)zero_ptrs_host[k] & 15) || zero_bytes_host[k] < 0 || (zero_bytes_host[k] & 15))
+        return COMO_ERR_ARG;
+      z.p[k] = (uint4*)zero_ptrs_host[k];
+      z.n16[k] = zero_bytes_host[k] / 16;
       if (z.n16[k] > most) most = z.n16[k];
     }
   }

@@ -1006,11 +1006,11 @@ int como_nn_upsample2x_f32(const float* in, float* out, int NC, int H, int W, co
   return COMO_OK;
 }
 
-int como_nn_normalize_f32(const float* in, float* out, int N, int HW, const float* mean3, const float* std3,
+int como_nn_normalize_f32(const float* in, float* out, int N, int HW, const float* mean3_host, const float* std3_host,
                           como_stream_t stream) {
-  if (!in || !out || !mean3 || !std3 || N <= 0 || HW <= 0) return COMO_ERR_ARG;
+  if (!in || !out || !mean3_host || !std3_host || N <= 0 || HW <= 0) return COMO_ERR_ARG;
   como::Norm3 nm;
-  for (int k = 0; k < 3; ++k) { nm.mean[k] = mean3[k]; nm.sd[k] = std3[k]; }
+  for (int k = 0; k < 3; ++k) { nm.mean[k] = mean3_host[k]; nm.sd[k] = std3_host[k]; }
   const long total = (long)N * 3 * HW;
   hipLaunchKernelGGL(como::normalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out,
                      HW, nm, total);

@@ -274,11 +274,12 @@ extern "C" {
 COMO_DEF_TRACKREF(f32, float)
 COMO_DEF_TRACKREF(f64, double)
 
-int como_track_reference_pyr_f32(const float* depth0, int H0, int W0, const float* kf_poses, int nk, int levels, const int* hw,
-                                 const float* const* K, const float* const* dI_dw, const float* const* vals, float* const* P_out,
-                                 uint8_t* const* mask_out, float* const* J_out, float border, float depth_thresh, como_stream_t stream) {
-  if (!depth0 || !kf_poses || !hw || !K || !dI_dw || !vals || !P_out || !mask_out || !J_out || nk <= 0 || levels < 1 || levels > 4 ||
-      H0 <= 0 || W0 <= 0)
+int como_track_reference_pyr_f32(const float* depth0, int H0, int W0, const float* kf_poses, int nk, int levels, const int* hw_host,
+                                 const float* const* K_host, const float* const* dI_dw_host, const float* const* vals_host,
+                                 float* const* P_out_host, uint8_t* const* mask_out_host, float* const* J_out_host, float border,
+                                 float depth_thresh, como_stream_t stream) {
+  if (!depth0 || !kf_poses || !hw_host || !K_host || !dI_dw_host || !vals_host || !P_out_host || !mask_out_host || !J_out_host ||
+      nk <= 0 || levels < 1 || levels > 4 || H0 <= 0 || W0 <= 0)
     return COMO_ERR_ARG;
   como::TrackRefPyr A;
   A.levels = levels;
@@ -288,8 +289,11 @@ int como_track_reference_pyr_f32(const float* depth0, int H0, int W0, const floa
     const int sh = levels - 1 - l;
     int h = H0, w = W0;
     for (int k = 0; k < sh; ++k) { h = (h + 1) / 2; w = (w + 1) / 2; }
-    if (hw[2 * l] != h || hw[2 * l + 1] != w || !K[l] || !dI_dw[l] || !vals[l] || !P_out[l] || !mask_out[l] || !J_out[l]) return COMO_ERR_ARG;
-    A.K[l] = K[l]; A.dI_dw[l] = dI_dw[l]; A.vals[l] = vals[l]; A.P[l] = P_out[l]; A.mask[l] = mask_out[l]; A.J[l] = J_out[l];
+    if (hw_host[2 * l] != h || hw_host[2 * l + 1] != w || !K_host[l] || !dI_dw_host[l] || !vals_host[l] || !P_out_host[l] ||
+        !mask_out_host[l] || !J_out_host[l])
+      return COMO_ERR_ARG;
+    A.K[l] = K_host[l]; A.dI_dw[l] = dI_dw_host[l]; A.vals[l] = vals_host[l];
+    A.P[l] = P_out_host[l]; A.mask[l] = mask_out_host[l]; A.J[l] = J_out_host[l];
     A.h[l] = h; A.w[l] = w; A.shift[l] = sh;
     A.block0[l] = blocks;
     blocks += (unsigned)(((long)h * w + 255) / 256);

@@ -135,12 +135,13 @@ int como_track_reference_f64(const double* depth, const double* rel, const doubl
 /* The tracker's whole reference pyramid in one launch (Tracking.update_kf_reference, como/odom/Tracking.py:187-313, with
  * pyr.depth_interp_mode nearest_neighbor, como/data/depth_resize.py:6-36): depth0 (nk,H0,W0) the finest depth images, kf_poses
  * (nk,4,4) world poses of the reference keyframes (the LAST one is the frame the points are expressed in: rel_b = T_last^-1 T_b);
- * levels <= 4 pyramid levels COARSE -> FINE, hw[2 l], hw[2 l + 1] their sizes (= the finest size pooled levels - 1 - l times:
- * checked), per level (host arrays of device pointers) K (3,3), dI_dw (nk,n,1,2), vals (nk,n,1) and the outputs P (nk,n,3),
- * mask (nk,n), J (nk,n,1,8) -- per pixel what como_track_reference_f32 writes. */
-int como_track_reference_pyr_f32(const float* depth0, int H0, int W0, const float* kf_poses, int nk, int levels, const int* hw,
-                                 const float* const* K, const float* const* dI_dw, const float* const* vals, float* const* P_out,
-                                 uint8_t* const* mask_out, float* const* J_out, float border, float depth_thresh, como_stream_t stream);
+ * levels <= 4 pyramid levels COARSE -> FINE, hw_host[2 l], hw_host[2 l + 1] their sizes (= the finest size pooled levels - 1 - l
+ * times: checked), per level (the *_host parameters: host arrays of device pointers) K (3,3), dI_dw (nk,n,1,2), vals (nk,n,1) and
+ * the outputs P (nk,n,3), mask (nk,n), J (nk,n,1,8) -- per pixel what como_track_reference_f32 writes. */
+int como_track_reference_pyr_f32(const float* depth0, int H0, int W0, const float* kf_poses, int nk, int levels, const int* hw_host,
+                                 const float* const* K_host, const float* const* dI_dw_host, const float* const* vals_host,
+                                 float* const* P_out_host, uint8_t* const* mask_out_host, float* const* J_out_host, float border,
+                                 float depth_thresh, como_stream_t stream);
 int como_reproject_depth_f32(const float* Tck, const float* K, const float* P, long n, int h, int w, void* order_ws, float* zbuf,
                              float* img, uint8_t* seen, int* nseen, como_stream_t stream);
 int como_reproject_depth_f64(const double* Tck, const double* K, const double* P, long n, int h, int w, void* order_ws,
@@ -438,11 +439,11 @@ typedef struct como_dr_fuse {
 int como_dense_ref_fused_f32(const float* Kt, long kt_slot_stride, const int* pixidx, const float* logzm, const float* Twc,
                              const float* K, const float* dlogzm_dTwc, int B, int n, int m, int Wimg, float* Pwn, float* dPwn_dTwc,
                              float* uvec, float* zbuf, float* logzn_out, void* hists, float* med_out3, const int* pixcoord, int flags,
-                             const como_dr_fuse* fuse, como_stream_t stream);
+                             const como_dr_fuse* fuse_host, como_stream_t stream);
 int como_dense_ref_fused_f64(const double* Kt, long kt_slot_stride, const int* pixidx, const double* logzm, const double* Twc,
                              const double* K, const double* dlogzm_dTwc, int B, int n, int m, int Wimg, double* Pwn, double* dPwn_dTwc,
                              double* uvec, double* zbuf, double* logzn_out, void* hists, double* med_out3, const int* pixcoord, int flags,
-                             const como_dr_fuse* fuse, como_stream_t stream);
+                             const como_dr_fuse* fuse_host, como_stream_t stream);
 
 /* Mapping.store_vars' full-image median depth (Mapping.py:749-758) WITHOUT re-reading all of K~ every GN iteration: instead of
  * the depth-only pass of como_dense_ref_* (flag 8) this evaluates z_n = exp(K~[n,:] logz_m) only for the pixels whose cached
@@ -683,7 +684,7 @@ int como_se3_compose_f64(const double* A, const double* B, double* out, int n, i
  *             2 LeakyReLU(residual + y) (ResidualConv.forward, layers.py:23-27); statistics either from `sums` (as
  *             accumulated by conv2d) or, when sums is NULL, computed here into stats (N*G*2 float scratch).
  *  maxpool2 : nn.MaxPool2d(2); upsample2x: nn.Upsample(scale 2, bilinear, align_corners=False);
- *  normalize: torchvision Normalize(mean, std) on 3 channels (mean3/std3 are HOST pointers);
+ *  normalize: torchvision Normalize(mean, std) on 3 channels (mean3_host / std3_host: 3 floats each);
  *  cov_act  : normalize_params_cov + kernel_params_to_covariance, (N,3,HW) -> (N,4,HW) = [x, s, s, z];
  *  resize_aa: F.interpolate(mode="bilinear", antialias=True, align_corners=False). */
 int como_nn_conv2d_f32(const float* in, const float* wt, const float* bias, float* out, int N, int Cin, int CinP, int Cout,
@@ -720,7 +721,7 @@ int como_nn_groupnorm_f32(const float* x, const float* gamma, const float* beta,
                           como_stream_t stream);
 int como_nn_maxpool2_f32(const float* in, float* out, int NC, int H, int W, como_stream_t stream);
 int como_nn_upsample2x_f32(const float* in, float* out, int NC, int H, int W, como_stream_t stream);
-int como_nn_normalize_f32(const float* in, float* out, int N, int HW, const float* mean3, const float* std3,
+int como_nn_normalize_f32(const float* in, float* out, int N, int HW, const float* mean3_host, const float* std3_host,
                           como_stream_t stream);
 int como_nn_cov_act_f32(const float* in, float* out, int N, int HW, como_stream_t stream);
 int como_nn_resize_aa_f32(const float* in, float* out, int NC, int Hi, int Wi, int Ho, int Wo, como_stream_t stream);
@@ -751,10 +752,11 @@ int como_frame_stack_f64(const void* rgb, int rgb_is_f32, int H, int W, double* 
 int como_img_blur_down_f32(const float* img, float* out, int NC, int H, int W, como_stream_t stream);
 /* The tracker's three-level image pyramid of one colour frame (3,H,W) in one launch (Tracking.prep_tracking_img,
  * /root/reference/como/odom/Tracking.py:103-107): gray (H,W), l1 = blur_down(gray), l2 = blur_down(l1) -- bit-identical to
- * como_rgb_to_gray_f32 + 2 x como_img_blur_down_f32; up to eight small buffers (16-byte aligned, multiples of 16 bytes) are cleared in
- * the same launch. */
-int como_track_frame_pyramid3_f32(const float* rgb, float* gray, float* l1, float* l2, int H, int W, void* const* zero_ptrs,
-                                  const long* zero_bytes, int n_zero, como_stream_t stream);
+ * como_rgb_to_gray_f32 + 2 x como_img_blur_down_f32; up to eight small buffers (zero_ptrs_host /
+ * zero_bytes_host: host arrays of n_zero device pointers and sizes; 16-byte aligned, multiples of 16 bytes) are cleared in the same
+ * launch. */
+int como_track_frame_pyramid3_f32(const float* rgb, float* gray, float* l1, float* l2, int H, int W, void* const* zero_ptrs_host,
+                                  const long* zero_bytes_host, int n_zero, como_stream_t stream);
 int como_img_blur_down_f64(const double* img, double* out, int NC, int H, int W, como_stream_t stream);
 /* img_blur: the same blur without decimation (GaussianBlurModule); depth_pool2: pyr_depth (como/data/depth_resize.py:6-36)
  * with kernel_size 2, mode 0 bilinear, 1 nearest_neighbor, 2 max, 3 min, 4 masked_bilinear. */
